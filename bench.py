@@ -19,6 +19,14 @@ barrier+synchronize brackets.  roofline.achieved = algorithmic bytes of one
 frame / the frame's GPU time (HIP events on the render stream bracketing all
 of the frame's kernels, rtx_kernel_time).  cpu_baseline = the CPU restatement (oracle/, "port") timed on this
 host's cores over row bands of the same frame.
+
+A plain run sets up, warms up, times the K frames and prints the line.
+`--full` adds what takes runs of its own: the latency frames
+(frame_latency_ms), the CPU baseline legs (cpu_baseline, cpu_baseline_O0,
+gpu_over_cpu), the parity block of the timed frame and, on N > 1 GPUs, the
+gather check; without it those fields are null.  `--dump-outputs DIR` writes
+the last timed frame (the 8-bit image the timed path leaves in HBM; N > 1:
+as rank 0 gathered it) to DIR/rgb8.npy as float32, height x width x 3.
 """
 import argparse
 import hashlib
@@ -357,7 +365,13 @@ def main():
     ap.add_argument("--scene", default=os.path.join(ROOT, "scenes", "trimesh2.ray"))
     ap.add_argument("--flags", default="-w 1920 -r 5 -O r -A 4")
     ap.add_argument("--tile", type=int, default=16)
-    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline figure: the latency frames, the CPU baseline legs, the parity block "
+                         "of the timed frame and (N > 1) the gather check")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last timed frame to DIR/rgb8.npy "
+                         "(height x width x 3, float32)")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baseline leg")
     ap.add_argument("--cpu-budget", type=float, default=10.0, help="seconds of CPU work per baseline run")
     ap.add_argument("--no-parity", action="store_true", help="skip the parity block of the timed frame")
     ap.add_argument("--traffic", default=os.path.join(ROOT, "profiles", "traffic_latest.json"),
@@ -479,36 +493,55 @@ def main():
     pipelined, renders = dev.overlap_count()
     n_ctx = dev.frame_contexts()
     # the last timed frame, for the byte comparison in the parity block
-    timed_rgb8 = rgb8.cpu().numpy() if world == 1 else None
-    # one frame alone (the frame before it finished, no overlap): the
-    # latency of a frame, beside the throughput of back-to-back frames
-    lat = []
-    for _ in range(3):
-        torch.cuda.synchronize()
-        if world > 1:
-            dist.barrier()
-        t1 = time.perf_counter()
-        step()
-        torch.cuda.synchronize()
-        lat.append((time.perf_counter() - t1) * 1e3)
-    frame_latency_ms = sorted(lat)[1]
-    dev.kernel_time()  # (not part of the roofline's frames)
-    if world > 1:
-        t = torch.tensor([frame_latency_ms], dtype=torch.float64, device=cdev)
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        frame_latency_ms = float(t.item())
-    dev.frame_status()  # (the latency frames too)
-    # N > 1: the gathered frame (the last one: every rank rendered its tiles
-    # into HBM on the overlapping frame contexts, rank 0 gathered them) against
-    # rank 0's own host-buffer render of the whole frame, byte for byte
-    gather_check = None
-    if world > 1 and rank == 0:
+    timed_rgb8 = rgb8.cpu().numpy() if world == 1 and (args.full or args.dump_outputs) else None
+
+    def gathered_frame():
+        """rank 0, N > 1: the frame as the last gather left it, tiles put back in place"""
         import numpy as np
 
         full = np.zeros((height, opts.width, 3), np.uint8)
         for r in range(world):
             n = pkg.shard_pixels(opts, height, tile, r, world, True) * 3
             pkg.unpack_tiles(gather_list[r][:n].cpu().numpy(), opts.width, height, tile, r, world, full)
+        return full
+
+    if args.dump_outputs and rank == 0:
+        # what the timed path handed back in its last step: the frame's 8-bit
+        # image (N > 1: as rank 0 gathered it), one file, 4 bytes per sample
+        import numpy as np
+
+        frame = timed_rgb8 if world == 1 else gathered_frame()
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "rgb8.npy"),
+                frame.reshape(height, opts.width, 3).astype(np.float32))
+    # one frame alone (the frame before it finished, no overlap): the
+    # latency of a frame, beside the throughput of back-to-back frames
+    frame_latency_ms = None
+    if args.full:
+        lat = []
+        for _ in range(3):
+            torch.cuda.synchronize()
+            if world > 1:
+                dist.barrier()
+            t1 = time.perf_counter()
+            step()
+            torch.cuda.synchronize()
+            lat.append((time.perf_counter() - t1) * 1e3)
+        frame_latency_ms = sorted(lat)[1]
+        dev.kernel_time()  # (not part of the roofline's frames)
+        if world > 1:
+            t = torch.tensor([frame_latency_ms], dtype=torch.float64, device=cdev)
+            dist.all_reduce(t, op=dist.ReduceOp.MAX)
+            frame_latency_ms = float(t.item())
+        dev.frame_status()  # (the latency frames too)
+    # N > 1: the gathered frame (the last one: every rank rendered its tiles
+    # into HBM on the overlapping frame contexts, rank 0 gathered them) against
+    # rank 0's own host-buffer render of the whole frame, byte for byte
+    gather_check = None
+    if args.full and world > 1 and rank == 0:
+        import numpy as np
+
+        full = gathered_frame()
         ref = dev.render(opts, want_f64=False)["rgb8"].reshape(full.shape)
         gather_check = {"rgb8_mismatch_pixels": int(np.count_nonzero(np.any(full != ref, axis=-1))),
                         "pixels": int(height * opts.width),
@@ -589,7 +622,7 @@ def main():
         for w in kernels.values():
             w["algorithmic_bytes"] = kernel_bytes(w)
         cpu, parity, cpu_o0 = None, None, None
-        if not args.no_cpu and world == 1:
+        if args.full and not args.no_cpu and world == 1:
             cpu = cpu_baseline(pkg, args.scene, opts, height, args.cpu_budget)
             band, threads = cpu.pop("_band"), cpu.pop("_threads")
             # BASELINE.md's optional context row: the restatement at the
@@ -600,7 +633,7 @@ def main():
                 parity = parity_block(pkg, dev, args.scene, opts, height, band, threads, timed_rgb8)
         line = {
             "metric": METRIC, "value": round(value, 3), "unit": "Mrays/s", "n_gpus": world,
-            "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 3),
+            "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 3), "full": args.full,
             "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f64",
             "data": "synthetic (procedural trimesh2 stand-in scene, tools/gen_scenes.py seed 2; reference scene absent)",
             "config": {"workload": f"trimesh2 {opts.width}x{height} {args.flags}", "scene": os.path.basename(args.scene),
@@ -648,7 +681,8 @@ def main():
             # other frame context while frame k finishes; ms_per_step is the
             # throughput, frame_latency_ms one frame rendered alone (render
             # + gather, max over ranks)
-            "frame_latency_ms": round(frame_latency_ms, 3),
+            # (--full only)
+            "frame_latency_ms": round(frame_latency_ms, 3) if frame_latency_ms is not None else None,
             # timed frames that ran pipelined on the frame contexts (how many
             # contexts: rtx_frame_contexts; rtx_overlap_count), and the frame
             # check of the timed frames

@@ -83,6 +83,46 @@ def test_bench_gpus_more_than_visible_fails_fast():
     assert time.monotonic() - t0 < 100
 
 
+def test_bench_options_listed():
+    r = _bench(["--help"])
+    assert r.returncode == 0
+    assert "--full" in r.stdout and "--dump-outputs" in r.stdout
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_dumps_the_timed_frame(tmp_path):
+    """A plain run (no --full) on a small frame: --steps sets the timed steps,
+    the line holds ms_per_step and none of the --full legs, and --dump-outputs
+    leaves the last timed frame — byte for byte the host-buffer render of the
+    same scene and flags — as DIR/rgb8.npy, float32, height x width x 3."""
+    import numpy as np
+
+    from conftest import load_package
+
+    flags = "-w 96 -r 3 -O r -A 2"
+    out = tmp_path / "dump"
+    r = _bench(["--gpus", "1", "--steps", "2", "--warmup", "1", "--flags", flags, "--dump-outputs", str(out)],
+               timeout=240)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    line = json.loads(lines[0])
+    assert line["steps"] == 2 and line["warmup"] == 1 and line["full"] is False
+    assert line["ms_per_step"] > 0 and line["value"] > 0
+    assert line["unit"] == "Mrays/s" and line["higher_is_better"] is True and line["dtype"] == "f64"
+    assert line["frame_check"]["bad_frames"] == 0
+    for leg in ("cpu_baseline", "cpu_baseline_O0", "parity", "frame_latency_ms", "gather_check"):
+        assert line[leg] is None
+    assert sorted(os.listdir(out)) == ["rgb8.npy"]
+    got = np.load(out / "rgb8.npy")
+    pkg = load_package()
+    opts = pkg.RenderOptions.from_cli(flags.split())
+    host = pkg.HostScene(os.path.join(ROOT, "scenes", "trimesh2.ray"))
+    ref = pkg.DeviceScene(host, 0).render(opts, want_f64=False)["rgb8"]
+    assert got.dtype == np.float32 and got.shape == (host.height_for(96), 96, 3)
+    assert np.array_equal(got, ref.reshape(got.shape).astype(np.float32))
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("n", [2, 4])
 def test_bench_ranks_rehearsal_on_one_gpu(n):
@@ -92,7 +132,7 @@ def test_bench_ranks_rehearsal_on_one_gpu(n):
     shard, rank 0 gathers them and prints one line with n_gpus 2 and the
     slowest rank's time; the line says it is a rehearsal."""
     t0 = time.monotonic()
-    r = _bench(["--gpus", str(n), "--no-cpu", "--steps", "2", "--warmup", "1"], timeout=240,
+    r = _bench(["--gpus", str(n), "--full", "--no-cpu", "--steps", "2", "--warmup", "1"], timeout=240,
                env={"RTX_BENCH_REHEARSAL": "1"})
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

@@ -1,5 +1,5 @@
 """Pins from the reference itself: its tokenizer and image I/O, compiled
-UNMODIFIED from /root/reference/ray/src (oracle/Makefile `ref`,
+UNMODIFIED from the reference's sources (oracle/Makefile `ref`,
 oracle/ref_harness.cpp -> oracle/_ref/libref_io.so), against the product's
 own (librtx_host.so):
 
@@ -10,34 +10,30 @@ own (librtx_host.so):
 * writeImage and rtx_write_image produce the same BMP bytes, and PNGs that
   both readers decode to the same pixels (pngimage.cpp:226-285).
 
-Build container only: /root/reference does not exist on the GPU box, so
-these tests skip there."""
+Where the reference's sources are present the reference is asked directly,
+and the record of its answers under tests/golden/ref_pins/
+(tools/make_ref_pins.py) must say the same.  Where they are absent the record
+stands in for it (tests/ref_pins.py), so the tests run everywhere."""
 import ctypes as C
 import glob
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import ref_pins as rp
 from conftest import GOLDEN, ROOT
-
-REF_SRC = "/root/reference/ray/src"
-REF_LIB = os.path.join(ROOT, "oracle", "_ref", "libref_io.so")
-
-pytestmark = pytest.mark.skipif(not os.path.isdir(REF_SRC), reason="reference sources absent (GPU box)")
 
 
 @pytest.fixture(scope="module")
 def ref():
-    subprocess.run(["make", "-C", os.path.join(ROOT, "oracle"), "ref"], check=True, capture_output=True)
-    L = C.CDLL(REF_LIB)
-    L.ref_tokens.argtypes = [C.c_char_p, C.c_char_p, C.c_int64, C.POINTER(C.c_int64)]
-    L.ref_read_image.argtypes = [C.c_char_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int64),
-                                 C.c_void_p, C.c_int64]
-    L.ref_write_image.argtypes = [C.c_char_p, C.c_int32, C.c_int32, C.c_void_p]
-    L.ref_last_error.restype = C.c_char_p
-    return L
+    """the reference's library, or None where only the record is there"""
+    return rp.load_ref() if rp.live() else None
+
+
+@pytest.fixture(scope="module")
+def pins():
+    return rp.pins()
 
 
 @pytest.fixture(scope="module")
@@ -47,12 +43,7 @@ def host(pkg):
     return L
 
 
-def _tokens(fn, path):
-    n = C.c_int64()
-    assert fn(path.encode(), None, 0, C.byref(n)) == 0
-    b = C.create_string_buffer(n.value)
-    assert fn(path.encode(), b, n.value, C.byref(n)) == 0
-    return b.value.decode(errors="replace").splitlines()
+_tokens = rp.tokens
 
 
 def _ray_fixtures():
@@ -67,39 +58,47 @@ def orc_tokens(pkg, orc):
     return orc.lib(pkg).oracle_tokens
 
 
+def _recorded(table, path):
+    """the record's entry for an input file, which must be the file recorded"""
+    rel = os.path.relpath(path, ROOT)
+    assert rel in table, f"{rel}: not in tests/golden/ref_pins/pins.json (tools/make_ref_pins.py records it)"
+    e = table[rel]
+    assert e["input_sha256"] == rp.file_sha(path), f"{rel} is not the file the record was taken from"
+    return e
+
+
 @pytest.mark.parametrize("path", _ray_fixtures(), ids=lambda p: os.path.relpath(p, ROOT))
-def test_token_stream_matches_reference(ref, host, orc_tokens, path):
+def test_token_stream_matches_reference(ref, pins, host, orc_tokens, path):
     """Both tokenizers, the product's (parser.cpp) and the checker's own
     (oracle/parse_restated.cpp), against the reference's."""
-    want = _tokens(ref.ref_tokens, path)
-    assert want[-1] == "EOF"
-    assert _tokens(host.rtx_host_tokens, path) == want
-    assert _tokens(orc_tokens, path) == want
+    got, got_orc = _tokens(host.rtx_host_tokens, path), _tokens(orc_tokens, path)
+    want_pin = _recorded(pins["tokens"], path)["tokens"]
+    if ref is not None:
+        want = _tokens(ref.ref_tokens, path)
+        assert want[-1] == "EOF"
+        assert got == want
+        assert got_orc == want
+        assert rp.token_pin(want) == want_pin  # the record is the reference's answer
+    else:
+        assert got[-1] == "EOF"
+        assert rp.token_pin(got) == want_pin
+        assert rp.token_pin(got_orc) == want_pin
 
 
-# edge cases of the scanner: comments, quoted identifiers, aliases, scalars
-# atof reads partially ('1-2', '1e', '--3', '.'), identifiers with '-',
-# reserved words without names in getNameForToken, syntax errors
-EDGE_TEXTS = {
-    "comments": "SBT-raytracer 1.0\n// line comment\n/* block\n comment */ camera { fov = 30; }\n",
-    "scalars": "1 -2 .5 -.25 1e3 1e-3 1e 1-2 --3 . 3.14159265358979323846 1e400 -0 007\n",
-    "idents": 'foo _bar a-b-c "quoted name" "with space" colour polymesh gennormals fov x1y2\n',
-    "punct": "( ) { } , = ;\n",
-    "no_newline_at_eof": "sphere { material = { diffuse = (0.1, 0.2, 0.3); } }",
-    "crlf": "SBT-raytracer 1.0\r\ncamera {\r\n position = (1,2,3);\r\n}\r\n",
-    "unterminated_string": 'name = "oops\n',
-    "unterminated_comment": "camera /* never closed\n",
-    "bad_char": "camera { position = (1, 2, 3) } @\n",
-    "slash_alone": "camera / 3\n",
-    "empty": "",
-}
+EDGE_TEXTS = rp.EDGE_TEXTS
 
 
 @pytest.mark.parametrize("name", list(EDGE_TEXTS))
-def test_token_edge_cases_match_reference(ref, host, orc_tokens, tmp_path, name):
+def test_token_edge_cases_match_reference(ref, pins, host, orc_tokens, tmp_path, name):
     p = tmp_path / f"{name}.ray"
     p.write_bytes(EDGE_TEXTS[name].encode())
-    want = _tokens(ref.ref_tokens, str(p))
+    e = pins["edge_tokens"][name]
+    assert e["text"] == EDGE_TEXTS[name]
+    if ref is not None:
+        want = _tokens(ref.ref_tokens, str(p))
+        assert e["tokens"] == want  # the record is the reference's answer
+    else:
+        want = e["tokens"]
     assert _tokens(host.rtx_host_tokens, str(p)) == want
     assert _tokens(orc_tokens, str(p)) == want
 
@@ -114,42 +113,51 @@ def _read(host, path):
     return out.reshape(h.value, w.value, ch.value)
 
 
-def _ref_read(ref, path):
-    """readImage: the pixels (h, w, channels).  readBMP's vector is height *
-    padded-row bytes long with the pixels packed at the front (bitmap.cpp:
-    57-91) — what TextureMap::getPixelAt reads, (x + y * width) * 3
-    (material.cpp:128-132); readPNG's is exactly rowbytes * height."""
-    w, h, n = C.c_int32(), C.c_int32(), C.c_int64()
-    if ref.ref_read_image(path.encode(), C.byref(w), C.byref(h), C.byref(n), None, 0) != 0:
-        return None
-    out = np.zeros(n.value, np.uint8)
-    assert ref.ref_read_image(path.encode(), C.byref(w), C.byref(h), C.byref(n), out.ctypes.data, out.size) == 0
-    npx = w.value * h.value
-    ch = 3 if path.lower().endswith(".bmp") else n.value // npx
-    return out[: npx * ch].reshape(h.value, w.value, ch)
+_ref_read = rp.ref_read
 
 
 def _image_fixtures():
-    return sorted(glob.glob(os.path.join(GOLDEN, "**", "*.bmp"), recursive=True) +
-                  glob.glob(os.path.join(GOLDEN, "**", "*.png"), recursive=True))
+    return sorted(p for p in glob.glob(os.path.join(GOLDEN, "**", "*.bmp"), recursive=True) +
+                  glob.glob(os.path.join(GOLDEN, "**", "*.png"), recursive=True)
+                  if os.path.dirname(p) != rp.PINS_DIR)  # (the record's own files: test_write_image_...)
 
 
 @pytest.mark.parametrize("path", _image_fixtures(), ids=lambda p: os.path.relpath(p, GOLDEN))
-def test_read_image_matches_reference(ref, host, path):
-    want = _ref_read(ref, path)
+def test_read_image_matches_reference(ref, pins, host, path):
     got = _read(host, path)
-    assert want is not None, ref.ref_last_error()
+    want_pin = _recorded(pins["images"], path)["pixels"]
+    assert want_pin is not None
     assert got is not None
-    assert got.shape == want.shape
-    assert np.array_equal(got, want), f"{int((got != want).sum())} bytes differ"
+    if ref is not None:
+        want = _ref_read(ref, path)
+        assert want is not None, ref.ref_last_error()
+        assert got.shape == want.shape
+        assert np.array_equal(got, want), f"{int((got != want).sum())} bytes differ"
+        assert rp.image_pin(want) == want_pin  # the record is the reference's answer
+    else:
+        assert list(got.shape) == want_pin["shape"]
+        assert rp.image_pin(got) == want_pin
 
 
 @pytest.mark.parametrize("ext", [".bmp", ".png"])
-@pytest.mark.parametrize("w,h", [(1, 1), (3, 2), (37, 19), (64, 64)])
-def test_write_image_matches_reference(ref, host, tmp_path, ext, w, h):
-    rgb = np.random.default_rng(w * 1000 + h).integers(0, 256, (h, w, 3), dtype=np.uint8)
+@pytest.mark.parametrize("w,h", rp.WRITE_SIZES)
+def test_write_image_matches_reference(ref, pins, host, tmp_path, ext, w, h):
+    rgb = rp.write_input(w, h)
+    e = pins["write"][rp.write_name(w, h, ext)]
+    assert e["input_sha256"] == rp.image_pin(rgb)["sha256"]
     a, b = str(tmp_path / f"ref{ext}"), str(tmp_path / f"rtx{ext}")
-    assert ref.ref_write_image(a.encode(), w, h, rgb.ctypes.data) == 0
+    recorded_a = open(os.path.join(rp.PINS_DIR, rp.write_name(w, h, ext)), "rb").read()
+    if ref is not None:
+        assert ref.ref_write_image(a.encode(), w, h, rgb.ctypes.data) == 0
+        if ext == ".bmp":  # (a PNG's bytes also depend on the zlib that packed it)
+            # the record is what the reference wrote (up to the last row's
+            # padding, which writeBMP reads from past its buffer: below)
+            fa = open(a, "rb").read()
+            n = len(fa) - (4 - w * 3 % 4) % 4
+            assert len(recorded_a) == len(fa) and recorded_a[:n] == fa[:n]
+    else:
+        with open(a, "wb") as f:
+            f.write(recorded_a)
     assert host.rtx_write_image(b.encode(), w, h, rgb.ctypes.data) == 0
     if ext == ".bmp":
         fa, fb = open(a, "rb").read(), open(b, "rb").read()
@@ -161,9 +169,18 @@ def test_write_image_matches_reference(ref, host, tmp_path, ext, w, h):
         n = len(fa) - pad
         assert fa[:n] == fb[:n]
         assert fb[n:] == bytes(pad)
-    for path in (a, b):
-        ri, hi = _ref_read(ref, path), _read(host, path)
-        assert ri is not None and hi is not None and np.array_equal(hi, ri)
+    for path, key in ((a, "ref_reads_ref"), (b, "ref_reads_rtx")):
+        hi = _read(host, path)
+        if ref is not None:
+            ri = _ref_read(ref, path)
+            assert ri is not None and hi is not None and np.array_equal(hi, ri)
+            assert rp.image_pin(ri) == e[key]  # the record is the reference's answer
+        else:
+            # (the reference's reading of the product's file was recorded on the
+            # bytes the product wrote then: the same bytes for a BMP, which the
+            # comparison above holds to the reference's; a PNG must decode to
+            # the writer's buffer, as the reference read it — checked below)
+            assert hi is not None and rp.image_pin(hi) == e[key]
         if ext == ".png":  # the buffer the writer was given
             assert np.array_equal(hi, rgb)
         # (readBMP compacts padded rows in place with out = in - offset, and

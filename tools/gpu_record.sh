@@ -4,7 +4,8 @@
 # the script.
 #   parity   pytest -m gpu (the whole GPU suite)
 #   smoke    __graft_entry__.smoke()
-#   bench    bench.py with the CPU leg and the parity block
+#   bench    bench.py --full: with the latency frames, the CPU leg and the
+#            parity block; its line goes to $RECORD_DIR (default record/)
 #   prof     rocprofv3 --kernel-trace --stats of the bench (3 frames + warmup)
 #   pmc      tools/profile_traffic.sh (FETCH / WRITE / TCC / SQ / VALU-mix
 #            passes, stamped with this build), then the bench again so its
@@ -16,6 +17,7 @@
 set -o pipefail
 cd "$GRAFT_REPO_ROOT"
 TAG=$1; shift
+REC=${RECORD_DIR:-record}
 mkdir -p gpurun_out
 for step in "$@"; do
   case $step in
@@ -28,9 +30,10 @@ for step in "$@"; do
         > gpurun_out/smoke_$TAG.log 2>&1 || { tail -5 gpurun_out/smoke_$TAG.log; exit 1; }
       tail -1 gpurun_out/smoke_$TAG.log ;;
     bench)
-      timeout -k 10 400 python -u bench.py > gpurun_out/bench_$TAG.json 2> gpurun_out/bench_$TAG.err \
-        || { tail -5 gpurun_out/bench_$TAG.err; exit 1; }
-      tail -1 gpurun_out/bench_$TAG.json | cut -c1-400 ;;
+      mkdir -p "$REC"
+      timeout -k 10 400 python -u bench.py --full > "$REC/bench_$TAG.json" 2> "$REC/bench_$TAG.err" \
+        || { tail -5 "$REC/bench_$TAG.err"; exit 1; }
+      tail -1 "$REC/bench_$TAG.json" | cut -c1-400 ;;
     prof)
       (cd /tmp && export TMPDIR=/tmp)
       export TMPDIR=/tmp
