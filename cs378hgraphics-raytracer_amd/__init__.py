@@ -27,6 +27,7 @@ BIN_DIR = os.path.join(PKG_DIR, "bin")
 REPO_ROOT = os.path.dirname(PKG_DIR)
 
 RTX_AA_NONE, RTX_AA_SUPERSAMPLE, RTX_AA_ADAPTIVE, RTX_AA_JITTERED = 0, 1, 2, 3
+RTX_QUERY_CLOSEST, RTX_QUERY_ALL, RTX_QUERY_KMAX = 0, 1, 64  # include/rtx_ray_query.h
 RTX_OK, RTX_ERR_INVALID, RTX_ERR_HIP, RTX_ERR_NODEVICE, RTX_ERR_CAPACITY, RTX_ERR_FRAME = 0, -1, -2, -3, -4, -5  # include/rtx.h
 
 
@@ -159,6 +160,8 @@ def hip_lib():
         lib.rtx_frame_status.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
         lib.rtx_overlap_count.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
         lib.rtx_frame_contexts.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
+        lib.rtx_query.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
+                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
         _hip = lib
     return _hip
 
@@ -167,6 +170,8 @@ def hip_lib():
 HIP_SYMBOLS = ["rtx_last_error", "rtx_device_count", "rtx_scene_create", "rtx_scene_destroy", "rtx_render",
                "rtx_shard_pixels", "rtx_kernel_time", "rtx_last_work", "rtx_frame_status", "rtx_overlap_count",
                "rtx_frame_contexts"]
+# ... and include/rtx_ray_query.h (ray queries: a header of its own, rtx.h is recorded byte for byte)
+HIP_QUERY_SYMBOLS = ["rtx_query"]
 HOST_SYMBOLS = ["rtx_host_last_error", "rtx_host_load", "rtx_host_desc", "rtx_host_info", "rtx_host_free",
                 "rtx_host_cubemap", "rtx_write_image", "rtx_image_height", "rtx_read_image", "rtx_shard_tiles",
                 "rtx_unpack_tiles", "rtx_host_tokens", "rtx_host_raw_records"]
@@ -419,6 +424,47 @@ class DeviceScene:
         n = C.c_int32()
         _check(lib.rtx_frame_contexts(self._s, C.byref(n)), lib, "rtx_frame_contexts")
         return n.value
+
+    QUERY_MODES = {"closest": RTX_QUERY_CLOSEST, "all": RTX_QUERY_ALL}
+
+    def query(self, P, D, mode: str = "closest", kmax: int = 16):
+        """Batched ray queries of the resident scene (rtx_query) for rays
+        (P[k], D[k]), world space (include/rtx_ray_query.h): mode "closest" — the closest hit of each
+        ray, one entry — or "all" — each ray's hits in the reference's sorted
+        order, the first kmax.  Synchronous, numpy in and out.  Returns
+        (t, object, face, nhits): (n, k) float64 / int32 / int32 and (n,)
+        int32, k = 1 for "closest" and kmax for "all" (the shapes of the CPU
+        restatement's query_batch); unused entries are t = 0, ids -1."""
+        lib = hip_lib()
+        m = self.QUERY_MODES[mode]
+        P = np.ascontiguousarray(P, np.float64)
+        D = np.ascontiguousarray(D, np.float64)
+        if P.ndim != 2 or P.shape[1] != 3 or D.shape != P.shape:
+            raise ValueError("query: P and D must both be (n, 3)")
+        n = P.shape[0]
+        k = 1 if m == RTX_QUERY_CLOSEST else int(kmax)
+        t = np.zeros((n, max(k, 0)), np.float64)
+        o = np.zeros((n, max(k, 0)), np.int32)
+        f = np.zeros((n, max(k, 0)), np.int32)
+        nh = np.zeros(n, np.int32)
+        rc = lib.rtx_query(self._s, m, n, P.ctypes.data, D.ctypes.data, k, t.ctypes.data, o.ctypes.data,
+                           f.ctypes.data, nh.ctypes.data, 0, None)
+        _check(rc, lib, "rtx_query")
+        return t, o, f, nh
+
+    def query_device(self, n: int, origins_ptr: int, dirs_ptr: int, mode: str = "closest", kmax: int = 16,
+                     t_ptr: int = 0, object_ptr: int = 0, face_ptr: int = 0, nhits_ptr: int = 0, stream: int = 0):
+        """Asynchronous rtx_query on device buffers (e.g. torch tensor
+        data_ptr()) on the given hipStream_t: origins / dirs (n, 3) float64;
+        t (n, k) float64, object / face (n, k) int32, nhits (n,) int32, each
+        optional (0); k = 1 for "closest", kmax for "all"."""
+        lib = hip_lib()
+        m = self.QUERY_MODES[mode]
+        k = 1 if m == RTX_QUERY_CLOSEST else int(kmax)
+        vp = lambda p: C.c_void_p(p) if p else None
+        rc = lib.rtx_query(self._s, m, n, vp(origins_ptr), vp(dirs_ptr), k, vp(t_ptr), vp(object_ptr),
+                           vp(face_ptr), vp(nhits_ptr), 1, vp(stream))
+        _check(rc, lib, "rtx_query")
 
     def close(self):
         if self._s:

@@ -2413,6 +2413,10 @@ __global__ void __launch_bounds__(WG) adapt_combine_kernel(const FrameParams* __
   }
 }
 
+// ============================================================ ray queries
+#define RTX_QUERY_KERNEL
+#include "rtx_query.h"
+
 // ============================================================ host side / C ABI
 namespace {
 
@@ -2567,6 +2571,18 @@ struct SceneState {
   size_t ev_used = 0;
   std::vector<hipEvent_t> ev_start, ev_stop;
   int64_t n_launch = 0;  // kernel launches since the last rtx_kernel_time
+  // rtx_query's own scratch (no render touches it): the claim counter, the
+  // short stacks' overflow columns, the host-pointer path's staging buffers
+  // (grown on demand, reused across calls), and the event that orders one
+  // query of the scene after the one before it, whatever their streams
+  struct QueryBuf {
+    void* p = nullptr;
+    size_t bytes = 0;
+  };
+  unsigned int* d_qclaim = nullptr;
+  QueryBuf q_ovf, q_rays, q_t, q_obj, q_face, q_nhits;
+  hipEvent_t q_ev = nullptr;
+  bool q_used = false;
 };
 
 template <typename T>
@@ -2938,6 +2954,10 @@ rtx_status rtx_scene_destroy(void* scene) {
     if (E.h) (void)hipHostFree(E.h);
     if (E.ev) (void)hipEventDestroy(E.ev);
   }
+  if (st->d_qclaim) (void)hipFree(st->d_qclaim);
+  for (SceneState::QueryBuf* b : {&st->q_ovf, &st->q_rays, &st->q_t, &st->q_obj, &st->q_face, &st->q_nhits})
+    if (b->p) (void)hipFree(b->p);
+  if (st->q_ev) (void)hipEventDestroy(st->q_ev);
   for (auto e : st->ev_pool) (void)hipEventDestroy(e);
   for (auto e : st->ev_start) (void)hipEventDestroy(e);
   for (auto e : st->ev_stop) (void)hipEventDestroy(e);
@@ -4453,6 +4473,157 @@ rtx_status rtx_kernel_time(void* scene, double* total_ms, int* launches) {
   st->n_launch = 0;
   st->ev_start.clear();
   st->ev_stop.clear();
+  return RTX_OK;
+}
+
+// a query scratch buffer of at least `bytes` (the caller orders its reuse)
+static rtx_status query_buf(SceneState::QueryBuf& b, size_t bytes) {
+  if (bytes <= b.bytes) return RTX_OK;
+  if (b.p) (void)hipFree(b.p);
+  b.p = nullptr;
+  b.bytes = 0;
+  HIP_TRY(hipMalloc(&b.p, bytes));
+  b.bytes = bytes;
+  return RTX_OK;
+}
+
+rtx_status rtx_query(void* scene, int32_t mode, int64_t n, const double* origins, const double* dirs, int32_t kmax,
+                     double* t, int32_t* object, int32_t* face, int32_t* nhits, int device_ptrs, void* stream_v) {
+  // the arguments first: nothing of the scene is read before they are valid
+  if (mode != RTX_QUERY_CLOSEST && mode != RTX_QUERY_ALL) {
+    g_err = "rtx_query: unknown mode (RTX_QUERY_CLOSEST or RTX_QUERY_ALL)";
+    return RTX_ERR_INVALID;
+  }
+  if (n < 0) {
+    g_err = "rtx_query: negative ray count";
+    return RTX_ERR_INVALID;
+  }
+  if (kmax < 1) {
+    g_err = "rtx_query: kmax must be at least 1";
+    return RTX_ERR_INVALID;
+  }
+  if (mode == RTX_QUERY_CLOSEST && kmax != 1) {
+    g_err = "rtx_query: a closest-hit query has one entry per ray (kmax must be 1)";
+    return RTX_ERR_INVALID;
+  }
+  if (n > 0 && (!origins || !dirs)) {
+    g_err = "rtx_query: null origins / dirs";
+    return RTX_ERR_INVALID;
+  }
+  if (!scene) {
+    g_err = "rtx_query: null scene";
+    return RTX_ERR_INVALID;
+  }
+  if (n > (int64_t(1) << 31)) {
+    g_err = "rtx_query: more than 2^31 rays in one call";
+    return RTX_ERR_CAPACITY;
+  }
+  if (kmax > RTX_QUERY_KMAX) {
+    g_err = "rtx_query: kmax above " + std::to_string(RTX_QUERY_KMAX);
+    return RTX_ERR_CAPACITY;
+  }
+  if (n == 0) return RTX_OK;
+  SceneState* st = static_cast<SceneState*>(scene);
+  HIP_TRY(hipSetDevice(st->device));
+  hipStream_t qs = static_cast<hipStream_t>(stream_v);
+  rtx_status rc = RTX_OK;
+  // stacks: the render's rule (render_once) at this kernel's own residency
+  const size_t lds_stacks = size_t(st->stack_cap) * 64 * sizeof(int) * WAVES_PER_WG;
+  const size_t lds_cold = size_t(RTX_COLD_FIELDS) * 64 * sizeof(double) * WAVES_PER_WG;
+  const size_t lds_full = lds_stacks + lds_cold;
+  int lds_k = RTX_LDS_STACK;
+  bool short_stack = st->stack_cap > lds_k && lds_full * RTX_QUERY_WAVES > size_t(160) * 1024;
+  if (const char* e = getenv("RTX_TEST_LDS_STACK"))
+    if (atoi(e) > 0) {
+      lds_k = std::min(atoi(e), 64);
+      short_stack = st->stack_cap > lds_k;
+    }
+  const size_t lds = short_stack ? size_t(lds_k) * 64 * sizeof(int) * WAVES_PER_WG + lds_cold : lds_full;
+  if (lds > 160 * 1024) {
+    g_err = "rtx_query: LDS budget exceeded (BVH too deep)";
+    return RTX_ERR_CAPACITY;
+  }
+  const bool all = mode == RTX_QUERY_ALL;
+  const void* kfn = all ? (short_stack ? reinterpret_cast<const void*>(query_kernel<Q_NEXT, true>)
+                                       : reinterpret_cast<const void*>(query_kernel<Q_NEXT, false>))
+                        : (short_stack ? reinterpret_cast<const void*>(query_kernel<Q_CLOSEST, true>)
+                                       : reinterpret_cast<const void*>(query_kernel<Q_CLOSEST, false>));
+  int per_cu = 0;
+  HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kfn, WG, lds));
+  if (per_cu < 1) per_cu = 1;
+  const int64_t grid_needed = ((n + 63) / 64 + WAVES_PER_WG - 1) / WAVES_PER_WG;
+  const int64_t grid = std::min<int64_t>(static_cast<int64_t>(st->n_cu) * per_cu, grid_needed);
+  // one query of a scene after the other: they share the scratch below
+  if (!st->q_ev) HIP_TRY(hipEventCreateWithFlags(&st->q_ev, hipEventDisableTiming));
+  if (st->q_used) HIP_TRY(hipStreamWaitEvent(qs, st->q_ev, 0));
+  if (!st->d_qclaim) HIP_TRY(hipMalloc(&st->d_qclaim, sizeof(unsigned int)));
+  const size_t ovf_bytes = short_stack ? size_t(st->stack_cap - lds_k) * size_t(grid) * WG * sizeof(int) : 0;
+  if (ovf_bytes > st->q_ovf.bytes) {  // (growing frees the columns: the query before must be done with them)
+    if (st->q_used) HIP_TRY(hipEventSynchronize(st->q_ev));
+    if ((rc = query_buf(st->q_ovf, ovf_bytes)) != RTX_OK) return rc;
+  }
+  QueryArgs A;
+  std::memset(&A, 0, sizeof(A));
+  A.n = static_cast<unsigned int>(n);
+  A.claim = st->d_qclaim;
+  A.stack_cap = st->stack_cap;
+  A.lds_k = lds_k;
+  A.leaf_k = 8;  // the render's (render_once; RTX_LEAF_K)
+  if (const char* e = getenv("RTX_LEAF_K"))
+    if (atoi(e) > 0) A.leaf_k = std::min(65, atoi(e));
+  A.ovf = static_cast<int*>(st->q_ovf.p);
+  A.out.kmax = kmax;
+  const size_t ne = size_t(n) * size_t(kmax);
+  if (device_ptrs) {
+    A.P = origins;
+    A.D = dirs;
+    A.out.t = t;
+    A.out.object = object;
+    A.out.face = face;
+    A.out.nhits = nhits;
+  } else {
+    // host arrays: staged through the scene's buffers (the last query that
+    // used them has finished: every host-pointer call ends synchronised, and
+    // this stream waits for q_ev)
+    if (st->q_used) HIP_TRY(hipEventSynchronize(st->q_ev));
+    if ((rc = query_buf(st->q_rays, size_t(n) * 6 * sizeof(double))) != RTX_OK) return rc;
+    if (t && (rc = query_buf(st->q_t, ne * sizeof(double))) != RTX_OK) return rc;
+    if (object && (rc = query_buf(st->q_obj, ne * sizeof(int32_t))) != RTX_OK) return rc;
+    if (face && (rc = query_buf(st->q_face, ne * sizeof(int32_t))) != RTX_OK) return rc;
+    if (nhits && (rc = query_buf(st->q_nhits, size_t(n) * sizeof(int32_t))) != RTX_OK) return rc;
+    double* d_p = static_cast<double*>(st->q_rays.p);
+    double* d_d = d_p + size_t(n) * 3;
+    HIP_TRY(hipMemcpyAsync(d_p, origins, size_t(n) * 3 * sizeof(double), hipMemcpyHostToDevice, qs));
+    HIP_TRY(hipMemcpyAsync(d_d, dirs, size_t(n) * 3 * sizeof(double), hipMemcpyHostToDevice, qs));
+    A.P = d_p;
+    A.D = d_d;
+    A.out.t = t ? static_cast<double*>(st->q_t.p) : nullptr;
+    A.out.object = object ? static_cast<int32_t*>(st->q_obj.p) : nullptr;
+    A.out.face = face ? static_cast<int32_t*>(st->q_face.p) : nullptr;
+    A.out.nhits = nhits ? static_cast<int32_t*>(st->q_nhits.p) : nullptr;
+  }
+  HIP_TRY(hipMemsetAsync(st->d_qclaim, 0, sizeof(unsigned int), qs));
+  // (not RTX_LAUNCH: a query is no part of a render's launch count)
+  if (all) {
+    if (short_stack) hipLaunchKernelGGL((query_kernel<Q_NEXT, true>), dim3(grid), dim3(WG), lds, qs, st->S, A);
+    else hipLaunchKernelGGL((query_kernel<Q_NEXT, false>), dim3(grid), dim3(WG), lds, qs, st->S, A);
+  } else {
+    if (short_stack) hipLaunchKernelGGL((query_kernel<Q_CLOSEST, true>), dim3(grid), dim3(WG), lds, qs, st->S, A);
+    else hipLaunchKernelGGL((query_kernel<Q_CLOSEST, false>), dim3(grid), dim3(WG), lds, qs, st->S, A);
+  }
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipEventRecord(st->q_ev, qs));
+  st->q_used = true;
+  if (!device_ptrs) {
+    if (t) HIP_TRY(hipMemcpyAsync(t, A.out.t, ne * sizeof(double), hipMemcpyDeviceToHost, qs));
+    if (object) HIP_TRY(hipMemcpyAsync(object, A.out.object, ne * sizeof(int32_t), hipMemcpyDeviceToHost, qs));
+    if (face) HIP_TRY(hipMemcpyAsync(face, A.out.face, ne * sizeof(int32_t), hipMemcpyDeviceToHost, qs));
+    if (nhits) HIP_TRY(hipMemcpyAsync(nhits, A.out.nhits, size_t(n) * sizeof(int32_t), hipMemcpyDeviceToHost, qs));
+    HIP_TRY(hipStreamSynchronize(qs));
+#ifdef RTX_BOUNDS_CHECK
+    return bounds_check_report();
+#endif
+  }
   return RTX_OK;
 }
 
